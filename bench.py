@@ -29,6 +29,10 @@ Prints ONE JSON line (rank 0).  Extra objects:
   cpu_baseline      SURVEY 8(d): the CPU oracle (oracle/theia_oracle.py, torch fp32) running BASELINE configs[0] exactly
                     (DeiT-tiny, dinov2-large, batch 8, 10 warm-up + 50 timed steps, median) on the host's physical cores;
                     rank 0, N == 1 only.  The base+5-teacher oracle step of self-check 1 is reported beside it.
+
+``--dump-outputs DIR`` (rank 0) writes what the last timed step computed: train -- main_loss, params (the master weights after
+that step's update) and grads (its gradients); forward_feature -- features.  Inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -96,7 +100,13 @@ def parse(argv=None):
     ap.add_argument("--teacher-dtype", default="auto", choices=["auto", "bf16", "fp32"],
                     help="dtype of the resident teacher features.  auto = SURVEY.md 8(d): bf16 for the throughput modes (bf16 / fp8 -- the "
                          "reference's features ARE bf16 values, data_utils.py:374-379), fp32 for --precision fp32")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs); the train step "
+                         "then starts its timed steps from the state left by the warm-up, so that equal arguments give equal outputs")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def log(msg):
@@ -358,6 +368,54 @@ def load_traffic(pfx, workload=TRAFFIC_WORKLOAD, teachers="cddsv"):
 _KERNEL_TRACE = None
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_SAMPLE = 1 << 22  # elements per dumped array at most (16 MB of float32): a whole dump stays under 64 MB
+
+
+def dump_outputs(out_dir, outputs):
+    """Each output -- a tensor, or a list of tensors read as one concatenated vector -- flattened and written as <out_dir>/<name>.npy,
+    float64 as float64 and anything else as float32.  An output of more than DUMP_SAMPLE elements is written at DUMP_SAMPLE positions
+    drawn with a fixed seed (ascending; the same positions whenever the output has the same size)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        flat = torch.cat([x.detach().reshape(-1) for x in t]) if isinstance(t, list) else t.detach().reshape(-1)
+        flat = flat if flat.dtype == torch.float64 else flat.float()
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            flat = flat[torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values.to(flat.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.cpu().numpy())
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(outputs)}")
+
+
+class StepState:
+    """What a train step hands to the next one: the fp32 master weights, the Adam moments and step counter, and with fp8 the delayed-
+    scaling maxima / scales and their step counter.  Taken after the warm-up and put back right before the timed steps, it keeps the
+    settle loop (which runs as many steps as the clocks need) from reaching the outputs of --dump-outputs."""
+
+    def __init__(self, opt, engine):
+        self.opt, self.engine, self.fp8 = opt, engine, engine.fp8
+        if engine.precision == "fp8" and self.fp8 is None:
+            raise SystemExit("--dump-outputs with --precision fp8 needs a warm-up step first (--warmup >= 1)")
+        self.saved = [t.clone() for t in self._tensors()]
+        self.step_count = opt.step_count
+        self.fp8_steps = None if self.fp8 is None else self.fp8.steps
+
+    def _tensors(self):
+        ts = [t for st in self.opt.flat_state for t in (st["p"], st["m"], st["v"])]
+        return ts + ([] if self.fp8 is None else [self.fp8.amax, self.fp8.scale, self.fp8.inv])
+
+    def restore(self):
+        from theia_amd import engine as engine_mod
+        for t, s in zip(self._tensors(), self.saved):
+            t.copy_(s)
+        self.opt.step_count = self.step_count
+        if self.fp8 is not None:
+            self.fp8.steps = self.fp8_steps
+        engine_mod.PARAM_EPOCH[0] += 1  # the operand copies of the weights are rebuilt from the restored masters
+
+
 # ------------------------------------------------------------------------------------------------ train-step bench
 _DIAG = {}  # what an N > 1 run knows about itself so far: printed with the error if a rank fails (review item 7)
 
@@ -516,6 +574,7 @@ def _main(argv=None):
         step()
         torch.cuda.synchronize()
         log(f"warmup step {i} done")
+    start_state = StepState(opt, model.engine) if args.dump_outputs else None
     # settle: a fresh process on a fresh box runs ~15-20 % slow for its first seconds (clock ramp / allocator growth; measured:
     # 70 vs 59 ms/step with 3 warm-up steps, 59.8 with 40).  Keep stepping, untimed, until 3 consecutive steps agree with
     # the previous 3 within 2 % (at most 60 extra steps), then time exactly --steps steps.
@@ -543,6 +602,9 @@ def _main(argv=None):
                             "work_conserving_tile_schedule": {"on": bool(ddp.dynamic_schedule), "autotune_ms_per_step": ddp.autotune_dynamic_ms}})
         log(f"CU reservation for the gradient exchange: ms/step per candidate {dp_tune} -> {ddp._reserve} CUs; work-conserving tile "
             f"schedule: {ddp.autotune_dynamic_ms} ms/step -> {'on' if ddp.dynamic_schedule else 'off'}")
+    if start_state is not None:
+        start_state.restore()
+        del start_state
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -559,6 +621,10 @@ def _main(argv=None):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     loss_val = float(last.detach().float().cpu())
+    if args.dump_outputs and rank == 0:
+        params = [p for _, p in model.named_parameters()]
+        dump_outputs(args.dump_outputs, {"main_loss": last, "params": params,
+                                         "grads": [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]})
     # host time to enqueue ONE step into empty queues (untimed extra steps): the floor the launch path puts under a step
     host_dt = 1e9
     for _ in range(3):
@@ -822,6 +888,8 @@ def forward_feature_main(args, rank, world, dev):
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"features": out})
     # host time of one streamed pass (what replaces ~110 launches per chunk) and the eager path beside it
     torch.cuda.synchronize()
     th = time.perf_counter()

@@ -1,4 +1,4 @@
-"""CPU: host-side pieces that need no GPU -- configuration composition (reference YAML tree, scientific notation),
+"""CPU: host-side pieces that need no GPU -- configuration composition (YAML tree of the reference's layout, scientific notation),
 bench.py's multi-GPU launcher path."""
 import json
 import os
@@ -8,7 +8,6 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_CONFIGS = "/root/reference/src/theia/configs"
 
 
 def test_compose_parses_scientific_notation_overrides():
@@ -28,11 +27,50 @@ def test_coerce_is_recursive_and_conservative():
     assert _coerce("e3") == "e3" and _coerce("1e") == "1e" and _coerce("0x1e3") == "0x1e3"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONFIGS), reason="the reference tree only exists in the build container")
-def test_compose_from_the_reference_yaml_tree():
-    """--config-path onto the reference's own configs: same groups / keys, floats where the YAML says 2e-3 / 1e-2."""
+def _write_yaml_tree(root, c):
+    """A --config-path tree in the reference's layout (configs/<group>/<option>.yaml), written from the built-in tree: frame_level.yaml
+    selects its target models through a nested `defaults` list, and its small floats are written as 2e-3 / 1e-2, which PyYAML (YAML 1.1)
+    reads as strings.  The files differ from the built-in tree where noted, so a match can only come from reading them."""
+    import yaml
+
+    def exp_notation(x):
+        if isinstance(x, dict):
+            return {k: exp_notation(v) for k, v in x.items()}
+        if isinstance(x, float) and 0 < abs(x) < 0.1:
+            return f"{x:.0e}".replace("e-0", "e-")  # 0.002 -> "2e-3"
+        return x
+
+    def write(group, option, body, text=None):
+        d = os.path.join(root, *group.split("/"))
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, option + ".yaml"), "w") as f:
+            f.write(text if text is not None else yaml.safe_dump(body, sort_keys=False))
+
+    for group, option in c.ROOT_DEFAULTS:
+        body = dict(c.GROUPS[group][option])
+        if group == "training":
+            nested = body.pop("__defaults__")
+            text = "defaults:\n" + "".join(f" - {g.split('/', 1)[1]}: {o}\n" for g, o in nested.items())
+            write(group, option, None, text + yaml.safe_dump(exp_notation(body), sort_keys=False))
+        else:
+            if group == "logging":
+                body["project"] = "theia-yaml-tree"  # not the built-in value
+            write(group, option, body)
+    # cddsv as in the built-in tree; cdiv (frame_level's default, overridden below) names a single teacher, unlike the built-in cdiv
+    write("training/target_models", "cddsv", c.GROUPS["training/target_models"]["cddsv"])
+    write("training/target_models", "cdiv", {"target_model_names": ["facebook/dinov2-large"], "target_model_weights": None})
+
+
+def test_compose_from_a_yaml_tree(tmp_path):
+    """--config-path onto a YAML tree of the reference's layout: same groups / keys, floats where the YAML says 2e-3 / 1e-2."""
+    import yaml
     from theia_amd.utils import config as c
-    cfg = c.compose(["training/target_models=cddsv", "model.backbone.backbone=facebook/deit-base-patch16-224"], config_path=REF_CONFIGS)
+    _write_yaml_tree(str(tmp_path), c)
+    raw = yaml.safe_load(open(tmp_path / "training" / "frame_level.yaml"))
+    assert raw["base_lr"] == "2e-3" and raw["lr_scheduler"]["warm_up_lr_start_factor"] == "1e-2"  # strings on disk
+    assert c.compose([], config_path=str(tmp_path)).training.target_models.target_model_names == ["facebook/dinov2-large"]
+    cfg = c.compose(["training/target_models=cddsv", "model.backbone.backbone=facebook/deit-base-patch16-224"], config_path=str(tmp_path))
+    assert cfg.logging.project == "theia-yaml-tree"
     assert isinstance(cfg.training.base_lr, float) and cfg.training.base_lr == 2e-3
     assert isinstance(cfg.training.lr_scheduler.warm_up_lr_start_factor, float)
     assert len(cfg.training.target_models.target_model_names) == 5
