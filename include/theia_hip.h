@@ -388,8 +388,9 @@ int theia_layernorm_chw_bwd_colsum_q8(const void* dy, const void* x, const float
 size_t theia_layernorm_chw_workspace_bytes(int b, int64_t E);
 
 /* ------------------------------------------------------------------------------------------------
- * K4: multi-head self-attention softmax(Q K^T / sqrt(dh)) V, dh = 64, whole sequence per workgroup
- * (modeling_vit.py:164-189).  qkv: [b, n, 3*D] (q | k | v, heads contiguous inside each);  o: [b, n, D];
+ * K4: multi-head self-attention softmax(Q K^T / sqrt(dh)) V, dh = 64, 1 <= n <= 8192 (modeling_vit.py:164-189).  n <= 256: the
+ * whole sequence per workgroup; n > 256 (or THEIA_ATTN_KERNEL=tiled): key-tiled kernels, whose outputs must not overlap their
+ * inputs.  qkv: [b, n, 3*D] (q | k | v, heads contiguous inside each);  o: [b, n, D];
  * lse: f32 [b, h, n] (log-sum-exp of the scaled scores, saved for backward).  delta_ws: f32 [b, h, n] scratch of the backward pass
  * (theia_attention_bwd_workspace_bytes; the bf16 path for n <= 208 computes dQ, dK and dV in one kernel and does not touch it).
  * ---------------------------------------------------------------------------------------------- */

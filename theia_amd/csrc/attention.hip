@@ -1,5 +1,6 @@
 // K4: multi-head self-attention for the ViT student (transformers modeling_vit.py:164-189), head_dim = 64,
-// n <= 256 tokens (197 for DeiT).  Round-1 kernels: whole K/V (resp. Q/dO) of one (image, head) live in LDS as
+// n <= 256 tokens (197 for DeiT) here; longer sequences go to the key-tiled kernels of attention_tiled.hip.
+// Round-1 kernels: whole K/V (resp. Q/dO) of one (image, head) live in LDS as
 // f32 rows of pitch 68 (conflict-free ds_read_b128), one wave64 per query (resp. key) row, f32 VALU math with
 // exact softmax -- attention is 1.6 % of the step's FLOPs; an MFMA version is the planned upgrade.
 //
@@ -13,6 +14,10 @@
 int theia_attention_fwd_mfma(const void* qkv, void* o, float* lse, int b, int n, int h, hipStream_t s);
 int theia_attention_bwd_mfma(const void* qkv, const void* o, const void* d_o, const float* lse, void* dqkv, float* delta,
                              int b, int n, int h, hipStream_t s);
+// key-tiled kernels for any n up to their cap (attention_tiled.hip): n > AT_MAXN, or every n under THEIA_ATTN_KERNEL=tiled
+int theia_attention_fwd_tiled(const void* qkv, void* o, float* lse, int b, int n, int h, int dtype, hipStream_t s);
+int theia_attention_bwd_tiled(const void* qkv, const void* o, const void* d_o, const float* lse, void* dqkv, float* delta, int b, int n,
+                              int h, int dtype, hipStream_t s);
 
 constexpr int AT_DH = 64;
 constexpr int AT_PITCH = 68;    // floats per LDS row
@@ -230,6 +235,16 @@ static int attn_nsplit(int bh, int n) {
     return s;
 }
 
+// THEIA_ATTN_KERNEL=tiled: the key-tiled kernels at every n and for both dtypes (A/B switch, read once per process)
+static bool attn_tiled_forced() {
+    static int forced = -1;
+    if (forced < 0) {
+        const char* e = getenv("THEIA_ATTN_KERNEL");
+        forced = (e != nullptr && strcmp(e, "tiled") == 0) ? 1 : 0;
+    }
+    return forced != 0;
+}
+
 extern "C" size_t theia_attention_bwd_workspace_bytes(int b, int n, int h) { return (size_t)b * n * h * sizeof(float); }
 
 // raise a kernel's dynamic-LDS limit to the largest supported footprint, once per kernel (keyed on its address)
@@ -247,9 +262,10 @@ static void set_lds(K kern, size_t) {
 
 extern "C" int theia_attention_fwd(const void* qkv, void* o, float* lse, int b, int n, int h, int dtype, void* stream) {
     THEIA_CHECK_ARG(qkv && o && lse, "theia_attention_fwd: null pointer");
-    THEIA_CHECK_ARG(b > 0 && h > 0 && n > 0 && n <= AT_MAXN, "theia_attention_fwd: n=%d must be in [1,%d]", n, AT_MAXN);
+    THEIA_CHECK_ARG(b > 0 && h > 0 && n > 0, "theia_attention_fwd: b=%d n=%d h=%d must be positive", b, n, h);
     THEIA_CHECK_ARG(dtype == THEIA_F32 || dtype == THEIA_BF16, "theia_attention_fwd: bad dtype");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (n > AT_MAXN || attn_tiled_forced()) return theia_attention_fwd_tiled(qkv, o, lse, b, n, h, dtype, s);  // checks its own cap
     if (dtype == THEIA_BF16 && n <= 208) return theia_attention_fwd_mfma(qkv, o, lse, b, n, h, s);  // matrix-core path
     const size_t lds = ((size_t)2 * n * AT_PITCH + AT_WAVES * (AT_DH + AT_MAXN)) * sizeof(float);
     const int ns = attn_nsplit(b * h, n);
@@ -267,9 +283,10 @@ extern "C" int theia_attention_fwd(const void* qkv, void* o, float* lse, int b, 
 extern "C" int theia_attention_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, void* dqkv,
                                    float* delta_ws, int b, int n, int h, int dtype, void* stream) {
     THEIA_CHECK_ARG(qkv && o && d_o && lse && dqkv && delta_ws, "theia_attention_bwd: null pointer");
-    THEIA_CHECK_ARG(b > 0 && h > 0 && n > 0 && n <= AT_MAXN, "theia_attention_bwd: n=%d must be in [1,%d]", n, AT_MAXN);
+    THEIA_CHECK_ARG(b > 0 && h > 0 && n > 0, "theia_attention_bwd: b=%d n=%d h=%d must be positive", b, n, h);
     THEIA_CHECK_ARG(dtype == THEIA_F32 || dtype == THEIA_BF16, "theia_attention_bwd: bad dtype");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (n > AT_MAXN || attn_tiled_forced()) return theia_attention_bwd_tiled(qkv, o, d_o, lse, dqkv, delta_ws, b, n, h, dtype, s);  // checks its own cap
     if (dtype == THEIA_BF16 && n <= 208) return theia_attention_bwd_mfma(qkv, o, d_o, lse, dqkv, delta_ws, b, n, h, s);
     const size_t lds1 =((size_t)2 * n * AT_PITCH + AT_WAVES * (2 * AT_DH + AT_MAXN)) * sizeof(float);
     const size_t lds2 = ((size_t)2 * n * AT_PITCH + AT_WAVES * (2 * AT_DH + 2 * AT_MAXN)) * sizeof(float);

@@ -618,7 +618,7 @@ class StudentEngine:
         interp = interpolate_pos_encoding and not (gh * gw == GRID * GRID and hh == ww)
         geo = self.geo224 if (gh, gw, interp) == (GRID, GRID, False) else Geometry(gh, gw, self.tok0, self.nreg, interp)
         if geo.ntok > MAX_TOKENS:
-            raise NotImplementedError(f"{hh}x{ww} input = {geo.ntok} tokens: the attention kernels hold at most {MAX_TOKENS}")
+            raise NotImplementedError(f"{hh}x{ww} input = {geo.ntok} tokens: the attention kernels take at most {MAX_TOKENS}")
         params = self._cached_params("vit", vit)
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
             return _BackboneFn.apply(self, img, channels_last, do_rescale, do_normalize, geo, *params)

@@ -25,7 +25,7 @@ PATCH = 16
 IMAGE = 224
 GRID = 14
 NTOK = 197          # tokens of the plain DeiT at 224x224: CLS + 14*14 patches
-MAX_TOKENS = 256    # sequence length the attention kernels hold in LDS
+MAX_TOKENS = 8192   # longest sequence the attention kernels take (key-tiled above 256 tokens)
 INIT_RANGE = 0.02  # ViTConfig.initializer_range
 
 
