@@ -480,8 +480,10 @@ __global__ __launch_bounds__(AF_THREADS) void attn_bwd_fused_kernel(const bf16_t
             }
             // The per-score arithmetic is what bounds this loop (exp2 at quarter rate + 5 more issue slots per score, 8 scores per lane and
             // tile), so everything that can leave it does.  dS = P (dP - delta) / 8: the 1/8 goes into V (dP = dO V^T) and delta, both exact
-            // (a power of two).  Keys beyond n need no select: their K and V fragments are zeros, so their P = exp2(-lse) and dS = -P delta / 8
-            // are finite, their dK / dV rows are not stored, and in dQ = dS K they meet the zero rows K is staged with.
+            // (a power of two).  Keys beyond n have zero K and V fragments, so their score is 0 and P = exp2(-lse * log2e): that overflows to
+            // +inf once lse < -88 (every score of the row strongly negative), and dS = -P delta is then +-inf (NaN where delta = 0).  Their
+            // dK / dV rows are not stored, but phase 2 would meet inf x 0 in dQ = dS K: the packed dS of such a lane is selected to zero
+            // before it is stored (4 selects per step, not per score; P needs none -- it only feeds the dV of its own key).
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
                 float v8[8];
@@ -517,7 +519,7 @@ __global__ __launch_bounds__(AF_THREADS) void attn_bwd_fused_kernel(const bf16_t
                         dsv[t][r] = pv * (da[r] - dq4[r]);
                     }
                 }
-                const uint4 pb = am_pack(p[0], p[1]), sb = am_pack(dsv[0], dsv[1]);
+                const uint4 pb = am_pack(p[0], p[1]), sb = am_keep(kok, am_pack(dsv[0], dsv[1]));  // keys beyond n: dS = 0 exactly (see above)
                 // dS for phase 2, stored [key][query]: this lane holds key krow x queries q0 + 4g + {0..3} (tile t = 0: sb.x/.y, t = 1: .z/.w) --
                 // two 8-byte writes (as [query][key] they were eight 2-byte ones); phase 2 reads it back through the transposing LDS read
                 {
