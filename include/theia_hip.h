@@ -438,6 +438,19 @@ int theia_feature_ingest_bf16(const uint16_t* x_chw, const float* mean, const fl
                               void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Nearest-neighbour row expansion of the MLP translator head (models/adapter_heads.py:96-102: F.interpolate(mode="nearest")
+ * between two Rearranges) on token-major rows.  src [b, hs*ws, C] -> dst [b, ht*wt, C]:
+ *   dst[b, y*wt + x, :] = src[b, hy(y)*ws + wx(x), :]
+ * with PyTorch's nearest index per axis: identity if in == out, i >> 1 if out == 2*in, else min(floor(i * (float)in/out), in-1)
+ * (float32 scale).  A copy of bit patterns: 16-byte vectors when C*esz % 16 == 0, element-wise otherwise.  dtype THEIA_F32 / THEIA_BF16.
+ * theia_nearest_rows_bwd is the adjoint: dx [b, hs*ws, C] = the sum of dy [b, ht*wt, C] over each source row's preimage (y ascending,
+ * then x), f32 accumulation, one rounding, zero for an empty preimage; no atomics (bit-reproducible).
+ * THEIA_ERR_INVALID for null pointers, non-positive sizes, an unknown dtype or an output that overlaps the input.
+ * ---------------------------------------------------------------------------------------------- */
+int theia_nearest_rows_fwd(const void* src, void* dst, int b, int hs, int ws, int ht, int wt, int C, int dtype, void* stream);
+int theia_nearest_rows_bwd(const void* dy, void* dx, int b, int hs, int ws, int ht, int wt, int C, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * elementwise helpers on `dtype` buffers
  * ---------------------------------------------------------------------------------------------- */
 int theia_add_inplace(void* dst, const void* src, int64_t n, int dtype, void* stream); /* dst += src */

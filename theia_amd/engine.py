@@ -3,6 +3,8 @@
     uint8 images --patchify/LUT--> patch GEMM (+bias +pos) --> 12 x {LN, QKV GEMM, attention, out-proj GEMM(+res),
     LN, FC1 GEMM(+GELU), FC2 GEMM(+res)} --> LN --> per-teacher heads {pad ConvT, LN_chw, conv/convT(+ReLU) x2,
     LN_chw, Linear} --> distillation loss
+    (translator="mlp": row LN --> adapter GEMM on the 196 patch rows --> per-teacher {GEMM(+ReLU) ..., GEMM} on those rows -->
+    nearest row expansion to the teacher grid --> distillation loss)
 
 The engine owns no parameters: it reads the fp32 master parameters held by ``RobotVisionFM`` (reference state_dict
 layout), derives the operand layouts the kernels want (bf16/f32 casts, [co][tap][ci] conv packs, transposes for
@@ -344,13 +346,22 @@ class StudentEngine:
             return []
         return [(t, tr.translator_heads[tr.legit_target_model_name_map[t]]) for t in tr.target_model_names]
 
+    @property
+    def mlp(self) -> bool:
+        """the translator is the MLP one (backbone adapter + MLP heads) rather than lconv"""
+        return getattr(getattr(self.rvfm, "translator", None), "kind", None) == "mlp"
+
     def _build_buckets(self) -> None:
-        """Backward-completion order: heads (in forward order), then backbone layer groups from the top down."""
+        """Backward-completion order: heads (in forward order), the MLP translator's backbone adapter (its gradient needs every
+        head's), then backbone layer groups from the top down."""
         self.buckets = []
         tr = getattr(self.rvfm, "translator", None)
         for t, hm in self.head_modules():
             pre = f"translator.translator_heads.{tr.legit_target_model_name_map[t]}."
             self.buckets.append(GradBucket(f"head:{t}", [(pre + n, p) for n, p in hm.named_parameters()]))
+        if self.mlp:
+            self.buckets.append(GradBucket("translator:adapter", [("translator.backbone_adapter." + n, p)
+                                                                  for n, p in tr.backbone_adapter.named_parameters()]))
         vit = self.rvfm.backbone.model
         # three-layer groups from the top; the LAST layers to finish (2, 1, 0 + embeddings) are buckets of their own: what is still
         # to be exchanged when backward ends is one layer (28 MB of fp32 for DeiT-base) instead of three + embeddings (88 MB)
@@ -440,6 +451,14 @@ class StudentEngine:
                 self._plans[ck] = ops.plan_convT3x3(C, 16, 2, 1, 0)
             elif key == "up64":
                 self._plans[ck] = ops.plan_convT3x3(C, 31, 2, 0, 1)
+            elif key.startswith("tok_in:"):  # MLP adapter: the 14x14 patch rows of [b, ntok, D] -> dense [b*196, H] (and its weight gradient)
+                H = int(key[7:])
+                self._plans[ck] = ops.rowmap([(0, 0, 0)], (GRID, GRID), (GRID, GRID), 1, D, geo.ntok * D, geo.tok0 * D, GRID, 1, 0, 0,
+                                             GRID * GRID * H, 0)
+            elif key.startswith("tok_out:"):  # its data gradient: dense [b*196, H] -> the patch rows of [b, ntok, D]
+                H = int(key[8:])
+                self._plans[ck] = ops.rowmap([(0, 0, 0)], (GRID, GRID), (GRID, GRID), 1, H, GRID * GRID * H, 0, GRID, 1, 0, 0,
+                                             geo.ntok * D, geo.tok0 * D)
             elif key == "patch":  # [b*P, 768] patch matrix -> token rows tok0 + p of h[b, ntok, D]
                 self._plans[ck] = ops.rowmap([(0, 0, 0)], (geo.gh, geo.gw), (geo.gh, geo.gw), 1, 768, geo.P * 768, 0, geo.gw, 1, 0, 0,
                                              geo.ntok * D, geo.tok0 * D)
@@ -502,7 +521,7 @@ class StudentEngine:
                 # from then on ONE launch re-quantises all of them (round 6: they were ~130 launches of a few us per step)
                 qb = ops.QuantBatch(device)
                 for k in [k for k, t in self._opcache.items() if t.dtype == torch.bfloat16 and t.dim() == 2 and not k.endswith(".f8")
-                          and t.shape[1] % 64 == 0 and t.shape[0] >= 64 and k != "patch.w" and t.is_contiguous()]:
+                          and t.shape[1] % 64 == 0 and t.shape[0] >= 64 and k not in ("patch.w", "tr.w", "tr.wT") and t.is_contiguous()]:
                     q, inv = self.fp8.quantize(self._opcache[k], "w:" + k)
                     self._opcache[k + ".f8"], self._opcache[k + ".inv"] = q, inv
                     i = self.fp8.slot("w:" + k)
@@ -579,8 +598,19 @@ class StudentEngine:
             cb.add_cast(L.mlp.fc2.weight, new(f"l{i}.w2", D, F))
             cb.add_transpose(L.mlp.fc2.weight, new(f"l{i}.w2T", F, D))
         C = D
+        if self.mlp:
+            lin = self.rvfm.translator.backbone_adapter["1"]
+            H = lin.weight.shape[0]
+            cb.add_cast(lin.weight, new("tr.w", H, C))
+            cb.add_transpose(lin.weight, new("tr.wT", C, H))
         for t, hm in self.head_modules():
             pf = f"h:{t}."
+            if hm.kind == "mlp":  # (no operand of an MLP head is named "w8T": _LossFn.backward looks that key up for lconv heads)
+                for i, lin in enumerate(hm.linears()):
+                    n_out, n_in = lin.weight.shape
+                    cb.add_cast(lin.weight, new(pf + f"m{i}", n_out, n_in))
+                    cb.add_transpose(lin.weight, new(pf + f"m{i}T", n_in, n_out))
+                continue
             if hm.kind == "cls":
                 Ct = hm.adapter["0"].weight.shape[0]
                 cb.add_cast(hm.adapter["0"].weight, new(pf + "w", Ct, C))
@@ -915,6 +945,8 @@ class StudentEngine:
             if t not in tr.legit_target_model_name_map:
                 raise KeyError(t)
         head_params: List[torch.nn.Parameter] = []
+        if self.mlp:
+            head_params += self._cached_params("translator:adapter", tr.backbone_adapter)
         for t in names:
             head_params += self._cached_params("head:" + t, tr.translator_heads[tr.legit_target_model_name_map[t]])
         if z.dtype != self.dtype:
@@ -972,6 +1004,8 @@ class StudentEngine:
             raise NotImplementedError(f"the translator heads take the 14x14 patch grid of a 224x224 input ({self.geo224.ntok} tokens), "
                                       f"got {NTOK} tokens (the reference's heads reshape to 14x14 too, adapter_heads.py:281)")
         z = z.contiguous()
+        if self.mlp:
+            return self._mlp_fwd(z, names, save)
         outs, saved = [], []
         for t in names:
             hm = self._head(t)
@@ -1007,6 +1041,8 @@ class StudentEngine:
         return tuple(outs), {"z": z if save else None, "heads": saved, "b": b}
 
     def _translator_bwd(self, saved, names: List[str], dpreds: Sequence[Optional[torch.Tensor]]) -> torch.Tensor:
+        if self.mlp:
+            return self._mlp_bwd(saved, names, dpreds)
         z = saved["z"]
         dev, T, C, b = z.device, self.dtype, self.D, saved["b"]
         oc = self._operands(dev)
@@ -1124,6 +1160,99 @@ class StudentEngine:
             if train:
                 self._bucket_done(bucket, side)
         return dz
+
+    # ================================================================== MLP translator
+    # reference feature_translators.py:80-88 + adapter_heads.py:119-126: LN -> Linear on every token, then per head (drop CLS) ->
+    # nearest interpolation to the target grid -> Linear (-> ReLU -> Linear)*.  Nearest interpolation copies rows and LN / the MLP act
+    # on each row alone, so here the adapter runs on the 196 patch rows only (the LayerNorm on all token rows, a row-wise pass, the
+    # GEMM reads the patch rows through a row map), each head's Linears on [b*196, .] rows, and only the head's output is expanded
+    # to the target grid.  Same values in any arithmetic; the backward reduces dpred onto the 196 rows first.
+    def _mlp_fwd(self, z: torch.Tensor, names: List[str], save: bool):
+        dev, T, C = z.device, self.dtype, self.D
+        oc = self._opcache
+        b, NTOK = z.shape[0], z.shape[1]
+        tr = self.rvfm.translator
+        ln, lin = tr.backbone_adapter["0"], tr.backbone_adapter["1"]
+        H = lin.weight.shape[0]
+        Mp = b * GRID * GRID
+        y, mean, rstd = ops.layernorm_fwd(z.view(b * NTOK, C), ln.weight, ln.bias, LN_EPS_HEAD)
+        A = torch.empty(Mp, H, dtype=T, device=dev)
+        ops.gemm_nt(y, oc["tr.w"], A, Mp, H, C, self._plan(f"tok_in:{H}"), C, H, bias=lin.bias)
+        outs, saved = [], []
+        for t in names:
+            hm = self._head(t)
+            pf = f"h:{t}."
+            lins = hm.linears()
+            x, acts = A, []
+            for i, li in enumerate(lins):
+                last = i + 1 == len(lins)
+                x = self._mm(x, pf + f"m{i}", li.bias, act=N.ACT_NONE if last else N.ACT_RELU)
+                if not last:
+                    acts.append(x)
+            Ht, Wt = hm.target_size[1], hm.target_size[2]
+            outs.append(ops.nearest_rows_fwd(x, GRID, GRID, Ht, Wt))
+            if save:
+                saved.append(acts)
+        sv = {"z": z, "y": y, "mean": mean, "rstd": rstd, "A": A, "heads": saved, "b": b} if save else {"heads": saved, "b": b}
+        return tuple(outs), sv
+
+    def _mlp_bwd(self, saved, names: List[str], dpreds: Sequence[Optional[torch.Tensor]]) -> torch.Tensor:
+        z, y, A, b = saved["z"], saved["y"], saved["A"], saved["b"]
+        dev, T, C = z.device, self.dtype, self.D
+        oc = self._operands(dev)
+        tr = self.rvfm.translator
+        ln, alin = tr.backbone_adapter["0"], tr.backbone_adapter["1"]
+        H = alin.weight.shape[0]
+        NTOK = z.shape[1]
+        Mp = b * GRID * GRID
+        need = ops.wgrad_splits(Mp, H, C) * H * (C + 1)
+        for t in names:
+            for li in self._head(t).linears():
+                n_out, n_in = li.weight.shape
+                need = max(need, ops.wgrad_splits(Mp, n_out, n_in) * n_out * (n_in + 1))
+        side = self._side_queue(dev, need)
+
+        def lin_grads(dy, x, mod, rmap=None):
+            if not (mod.weight.requires_grad or mod.bias.requires_grad):
+                return
+            gw, accw = self._grad(mod.weight)
+            gb, accb = self._grad(mod.bias)
+            side.run(lambda: ops.linear_wgrad(dy, x, gw, accw, side.ws, bias=(gb, accb), rmap=rmap), dy, x)
+
+        dA = None  # sum over the heads, in the order of `names`
+        for hi, t in enumerate(names):
+            dp = dpreds[hi]
+            acts = saved["heads"][hi]
+            saved["heads"][hi] = None
+            if dp is None:
+                continue
+            hm = self._head(t)
+            pf = f"h:{t}."
+            if dp.dtype != T:
+                raise TypeError(f"gradient dtype {dp.dtype} does not match the engine's compute dtype {T}")
+            Ht, Wt = hm.target_size[1], hm.target_size[2]
+            lins = hm.linears()
+            d = ops.nearest_rows_bwd(dp.contiguous(), GRID, GRID, Ht, Wt).view(Mp, lins[-1].weight.shape[0])
+            for i in range(len(lins) - 1, -1, -1):
+                lin_grads(d, A if i == 0 else acts[i - 1], lins[i])
+                if i > 0:  # through the ReLU: relu(x) > 0 <=> x > 0, so the saved post-ReLU output is the mask
+                    d = self._mm(d, pf + f"m{i}T", act=N.ACT_MUL_DRELU, aux_in=acts[i - 1])
+                else:
+                    dA = self._mm(d, pf + "m0T", resid=dA)
+            del acts, d
+            if lins[0].weight.requires_grad:
+                self._bucket_done(self._bucket_of[id(lins[0].weight)][0], side)
+        if dA is None:
+            return torch.zeros(b, NTOK, C, dtype=T, device=dev)
+        lin_grads(dA, y, alin, self._plan(f"tok_in:{H}"))
+        # CLS and register rows of the LayerNorm's output gradient stay zero, so their rows of dz come out exactly zero
+        dy = torch.zeros(b * NTOK, C, dtype=T, device=dev)
+        ops.gemm_nt(dA, oc["tr.wT"], dy, Mp, C, H, self._plan(f"tok_out:{H}"), H, C)
+        ws = self.ws(N.lib().theia_layernorm_bwd_workspace_bytes(b * NTOK, C) // 4, dev)
+        dz = self._ln_bwd(dy, z.view(b * NTOK, C), ln, saved["mean"], saved["rstd"], None, ws)
+        if alin.weight.requires_grad:
+            self._bucket_done(self._bucket_of[id(alin.weight)][0], side)
+        return dz.view(b, NTOK, C)
 
     # ================================================================== loss
     def distill_loss(self, pred: torch.Tensor, target: torch.Tensor, head: Optional[str] = None) -> torch.Tensor:

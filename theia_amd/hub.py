@@ -50,6 +50,13 @@ def _target_sizes(cfg: Dict[str, Any]) -> Optional[Dict[str, tuple]]:
     return None
 
 
+def translator_kwargs_of(tr) -> Dict[str, Any]:
+    """the translator_kwargs that rebuild this translator (what build_feature_translator took besides the feature sizes)"""
+    if getattr(tr, "kind", "lconv") == "mlp":
+        return {"translator_hidden_size": int(tr.translator_hidden_size), "translator_n_layer": int(tr.translator_n_layer)}
+    return {"hidden_size_factor": float(tr.hidden_size_factor)}
+
+
 class TheiaModel(RobotVisionFM):
     """``RobotVisionFM`` with ``from_pretrained`` / ``save_pretrained`` on a hub-layout directory."""
 
@@ -107,7 +114,9 @@ class TheiaModel(RobotVisionFM):
     def save_pretrained(self, path: str, safe_serialization: bool = True) -> None:
         os.makedirs(path, exist_ok=True)
         cfg = dict(getattr(self, "config", {}))
-        cfg.update({"model_type": "theia", "backbone": self.backbone.model_name, "translator": "lconv",
+        tr = getattr(self, "translator", None)
+        cfg.update({"model_type": "theia", "backbone": self.backbone.model_name, "translator": getattr(tr, "kind", "lconv"),
+                    "translator_kwargs": translator_kwargs_of(tr) if tr is not None else cfg.get("translator_kwargs", {}),
                     "target_feature_sizes": {k: list(v) for k, v in (self.target_feature_sizes or {}).items()},
                     "feature_reduce_method": self.feature_reduce_method, "image_size": self.image_size})
         json.dump(cfg, open(os.path.join(path, CONFIG_NAME), "w"), indent=1)

@@ -386,17 +386,19 @@ def conv_wgrad(plan: ConvPlan, dy: torch.Tensor, x: torch.Tensor, b: int, C: int
 
 
 def linear_wgrad(dy: torch.Tensor, x: torch.Tensor, grad_w: torch.Tensor, accumulate: bool,
-                 ws: Optional[torch.Tensor] = None, bias: Optional[Tuple[torch.Tensor, bool]] = None) -> None:
+                 ws: Optional[torch.Tensor] = None, bias: Optional[Tuple[torch.Tensor, bool]] = None,
+                 rmap: Optional[RowMap] = None) -> None:
     """grad_w[N,K] (+)= dy[M,N]^T @ x[M,K];  bias = (grad_b, accumulate): grad_b[N] (+)= colsum(dy), inside the GEMM launch
-    when the kernel supports it, else with theia_colsum."""
+    when the kernel supports it, else with theia_colsum.  rmap: x is read through the input side of this row map (a dense dy
+    through its output side) instead of as a plain [M, K] matrix -- e.g. the patch rows of a token matrix."""
     M, Nn = dy.shape
-    K = x.shape[1]
+    K = x.shape[1] if rmap is None else rmap.in_c
     splits = wgrad_splits(M, Nn, K)
     need = splits * Nn * K
     extra = splits * Nn
     if ws is None or ws.numel() < need + extra:
         ws = torch.empty(need + extra, dtype=torch.float32, device=dy.device)
-    fused = gemm_wgrad(dy, x, ws, M, Nn, dy.stride(0), 1, splits, rm_plain(K, x.stride(0), dy.stride(0)),
+    fused = gemm_wgrad(dy, x, ws, M, Nn, dy.stride(0), 1, splits, rm_plain(K, x.stride(0), dy.stride(0)) if rmap is None else rmap,
                        bias[0] if bias is not None else None, bias[1] if bias is not None else False, ws[need:need + extra], defer_bias=True)
     wgrad_finish(ws, splits, Nn, 1, K, grad_w, K, 0, 1, accumulate, (ws[need:need + extra], bias[0], bias[1]) if fused else None)
     if bias is not None and not fused:
@@ -732,6 +734,30 @@ def feature_norm_bf16(x_bf16: torch.Tensor, mean: torch.Tensor, std: torch.Tenso
     out = torch.empty(rows, Cc, dtype=torch.float32, device=x_bf16.device)
     N.check(N.lib().theia_feature_norm_bf16(x_bf16.data_ptr(), mean.data_ptr(), std.data_ptr(), out.data_ptr(), rows, Cc,
                                             N.stream_ptr()), "theia_feature_norm_bf16")
+    return out
+
+
+def nearest_rows_fwd(src: torch.Tensor, hs: int, ws: int, ht: int, wt: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src [b, hs*ws, C] (or [b*hs*ws, C]) -> [b, ht*wt, C]: F.interpolate(mode="nearest") of the [b, C, hs, ws] map, token-major"""
+    C = src.shape[-1]
+    b = src.numel() // (hs * ws * C)
+    assert src.is_contiguous() and b * hs * ws * C == src.numel()
+    if out is None:
+        out = torch.empty(b, ht * wt, C, dtype=src.dtype, device=src.device)
+    N.check(N.lib().theia_nearest_rows_fwd(src.data_ptr(), out.data_ptr(), b, hs, ws, ht, wt, C, _dt(src), N.stream_ptr()),
+            "theia_nearest_rows_fwd")
+    return out
+
+
+def nearest_rows_bwd(dy: torch.Tensor, hs: int, ws: int, ht: int, wt: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """adjoint of nearest_rows_fwd: dy [b, ht*wt, C] -> [b, hs*ws, C], each source row the sum over its preimage"""
+    C = dy.shape[-1]
+    b = dy.numel() // (ht * wt * C)
+    assert dy.is_contiguous() and b * ht * wt * C == dy.numel()
+    if out is None:
+        out = torch.empty(b, hs * ws, C, dtype=dy.dtype, device=dy.device)
+    N.check(N.lib().theia_nearest_rows_bwd(dy.data_ptr(), out.data_ptr(), b, hs, ws, ht, wt, C, _dt(dy), N.stream_ptr()),
+            "theia_nearest_rows_bwd")
     return out
 
 

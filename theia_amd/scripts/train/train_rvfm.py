@@ -216,7 +216,12 @@ def ddp_main(cfg) -> dict:
                 target_feature_sizes[t + "_cls"] = get_model_feature_size(t, keep_spatial=True)[:1]
                 target_model_names.append(t + "_cls")
 
-    rvfm = RobotVisionFM(translator=cfg.model.translator.type, translator_kwargs=cfg.model.translator.kwargs,
+    translator_kwargs = dict(cfg.model.translator.kwargs)
+    if cfg.model.translator.type == "mlp" and "hidden_size" in translator_kwargs:
+        # the reference's configs/model/translator/mlp.yaml names the width `hidden_size`, which MLPFeatureTranslator
+        # (models/feature_translators.py:91-103) does not take: its own config fails with a TypeError.  Renamed here only.
+        translator_kwargs["translator_hidden_size"] = translator_kwargs.pop("hidden_size")
+    rvfm = RobotVisionFM(translator=cfg.model.translator.type, translator_kwargs=translator_kwargs,
                          target_feature_sizes=target_feature_sizes,
                          target_loss_weights=cfg.training.target_models.target_model_weights,
                          precision=cfg.get("precision", None), **cfg.model.backbone)

@@ -53,7 +53,9 @@ GROUPS: Dict[str, Dict[str, Any]] = {
                       "train_steps_per_epoch": 20, "eval_steps_per_epoch": 2},
     },
     "model/backbone": {"deit": {"backbone": "facebook/deit-small-patch16-224", "pretrained": False}},
-    "model/translator": {"lconv": {"type": "lconv", "kwargs": {"hidden_size_factor": 1.0}}},
+    # mlp: as the reference's configs/model/translator/mlp.yaml reads (scripts/train/train_rvfm.py renames `hidden_size`)
+    "model/translator": {"lconv": {"type": "lconv", "kwargs": {"hidden_size_factor": 1.0}},
+                         "mlp": {"type": "mlp", "kwargs": {"translator_n_layer": 3, "hidden_size": 1024}}},
     "training": {
         "frame_level": {
             "epochs": 50, "warm_up_steps_ratio": 0.1, "base_lr": 2e-3, "batch_size": 16, "random_target_models": -1,
