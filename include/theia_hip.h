@@ -273,6 +273,54 @@ typedef struct {
 int theia_quantize_fp8_batch(const theia_quant_job_t* jobs_device, int njobs, int64_t total_blocks, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * OCP MX fp8 (MXFP8) operands and the block-scaled GEMM of precision="mxfp8" (csrc/gemm_mx8.hip).  Replaces aten::linear of
+ * the ViT's q/k/v, fc1 and fc2 and the data-gradients of fc1 / fc2 (transformers modeling_vit.py:202-205,246-247).
+ * Format: blocks of 32 consecutive elements along K inside one row.  Per block amax = max |x| (x as stored, bf16 or f32);
+ * amax == 0: scale byte 127 and 32 zero bytes; otherwise e = clamp(floor(log2 amax) - 8, -127, 127), scale byte = e + 127
+ * (E8M0: 2^e), element = e4m3fn(RNE(clamp(x * 2^-e, -448, 448))).  Elements uint8 [rows, K] (row pitch K for the quantiser's
+ * output, `ld*` for GEMM operands), scales uint8 [rows, K/32] row-major.  Deterministic; no host-side state.
+ * ---------------------------------------------------------------------------------------------- */
+/* src [rows, K] (row pitch ld elements, 16-byte aligned rows; THEIA_F32 / THEIA_BF16) -> dst [rows, K], dst_scale [rows, K/32];
+ * K a positive multiple of 32 */
+int theia_quantize_mx8(const void* src, int src_dtype, int64_t rows, int K, int64_t ld, uint8_t* dst, uint8_t* dst_scale, void* stream);
+/* the same for a whole table of tensors in ONE launch (the MX copies of the weight operands after an optimizer step).
+ * theia_quantize_mx8_batch_plan validates a HOST table, fills first_block and returns the grid size (< 0: bad table); the table is
+ * then copied to the device once and reused while pointers and sizes stay the same. */
+typedef struct {
+    const void* src;    /* [rows, ld] elements of src_dtype */
+    uint8_t* dst;       /* e4m3 [rows, K] */
+    uint8_t* dst_scale; /* E8M0 [rows, K/32] */
+    int64_t rows;
+    int32_t K;
+    int32_t src_dtype;
+    int64_t ld;
+    int64_t first_block;
+} theia_mx8_job_t;
+int64_t theia_quantize_mx8_batch_plan(theia_mx8_job_t* jobs_host, int njobs);
+int theia_quantize_mx8_batch(const theia_mx8_job_t* jobs_device, int njobs, int64_t total_blocks, void* stream);
+/* out[m, n] = act( sum_k A[m, k] W[n, k] + bias[n] ) + resid[m, n] with A and W in the format above, f32 accumulation on
+ * v_mfma_scale_f32_16x16x128_f8f6f4, bf16 output.  The epilogue (bias, act, aux_in / aux_out, resid; all bf16, output-indexed with
+ * pitch ldo) is theia_gemm_nt's, with the same arithmetic and rounding.  Plain row-major operands; no atomics, no split-K: results
+ * are bit-reproducible.  Requirements: 1 <= M < 2^24, N a positive multiple of 8, K a positive multiple of 32, lda / ldw >= K and
+ * multiples of 16, ldo >= N and a multiple of 8, every tensor 16-byte aligned, aux_in with ACT_MUL_*, aux_out with ACT_GELU only. */
+typedef struct theia_gemm_mx8_args {
+    const uint8_t* a;       /* e4m3 [M, lda] */
+    const uint8_t* a_scale; /* E8M0 [M, K/32] */
+    const uint8_t* w;       /* e4m3 [N, ldw] */
+    const uint8_t* w_scale; /* E8M0 [N, K/32] */
+    void* out;              /* bf16 [M, ldo] */
+    const float* bias;      /* [N] or NULL */
+    const void* resid;      /* bf16, output-indexed, or NULL */
+    const void* aux_in;     /* bf16, output-indexed (ACT_MUL_*) or NULL */
+    void* aux_out;          /* bf16, output-indexed (ACT_GELU pre-activation) or NULL */
+    int32_t M, N, K;
+    int32_t lda, ldw, ldo;
+    int32_t act;
+    int32_t reserved;
+} theia_gemm_mx8_args_t;
+int theia_gemm_nt_mx8(const theia_gemm_mx8_args_t* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Parameter preparation (fp32 master weights in the reference state_dict layout -> operand layouts)
  * ---------------------------------------------------------------------------------------------- */
 /* dst[i] = cast(src[i]) ; dst has `dtype` elements */

@@ -73,6 +73,21 @@ class QuantJob(C.Structure):  # theia_quant_job_t
                 ("first_block", C.c_int32), ("pad_", C.c_int32)]
 
 
+class Mx8Job(C.Structure):  # theia_mx8_job_t
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("dst_scale", C.c_void_p), ("rows", C.c_int64), ("K", C.c_int32),
+                ("src_dtype", C.c_int32), ("ld", C.c_int64), ("first_block", C.c_int64)]
+
+
+class Mx8GemmArgs(C.Structure):  # theia_gemm_mx8_args_t
+    _fields_ = [
+        ("a", C.c_void_p), ("a_scale", C.c_void_p), ("w", C.c_void_p), ("w_scale", C.c_void_p), ("out", C.c_void_p),
+        ("bias", C.c_void_p), ("resid", C.c_void_p), ("aux_in", C.c_void_p), ("aux_out", C.c_void_p),
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+        ("lda", C.c_int32), ("ldw", C.c_int32), ("ldo", C.c_int32),
+        ("act", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class WgradFinishJob(C.Structure):
     """theia_wgrad_finish_job_t"""
     _fields_ = [("slabs", C.c_void_p), ("out", C.c_void_p), ("bias_slabs", C.c_void_p), ("bias_out", C.c_void_p), ("sn", C.c_int64),
@@ -127,6 +142,10 @@ _SIGNATURES = {
     "theia_distill_loss_bwd_q8": (C.c_int, [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int64, C.c_int, C.POINTER(Q8Out), C.c_void_p]),
     "theia_quantize_fp8_batch_plan": (C.c_int64, [C.c_void_p, C.c_int]),
     "theia_quantize_fp8_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+    "theia_quantize_mx8": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "theia_quantize_mx8_batch_plan": (C.c_int64, [C.c_void_p, C.c_int]),
+    "theia_quantize_mx8_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+    "theia_gemm_nt_mx8": (C.c_int, [C.POINTER(Mx8GemmArgs), C.c_void_p]),
     "theia_colsum_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "theia_cast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "theia_cast_batch_plan": (C.c_int64, [C.c_void_p, C.c_int]),

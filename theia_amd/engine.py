@@ -32,6 +32,9 @@ PARAM_EPOCH = [0]
 
 LN_EPS_VIT = 1e-12   # ViTConfig.layer_norm_eps
 LN_EPS_HEAD = 1e-5   # nn.LayerNorm default (adapter_heads.py:306-324)
+# precision="mxfp8": the operands of each layer that get MX fp8 copies -- q/k/v and fc1 / fc2 forward (W), fc2's and fc1's
+# data-gradients (W^T).  o_proj and the q/k/v data-gradient keep their bf16 operands
+MX8_WEIGHTS = ("wqkv", "w1", "w2", "w2T", "w1T")
 
 
 def preprocess_lut(do_rescale: bool, do_normalize: bool, mean: Sequence[float], std: Sequence[float]) -> np.ndarray:
@@ -311,9 +314,10 @@ class GradBucket:
 
 class StudentEngine:
     def __init__(self, rvfm, precision: str = "fp32"):
-        if precision not in ("fp32", "bf16", "fp8"):
-            raise ValueError("precision must be 'fp32' (exact-f32 MFMA, parity mode), 'bf16' (throughput mode) or 'fp8' (bf16 "
-                             "activations, e4m3 operands for the forward / data-gradient GEMMs, bf16 weight-gradient GEMMs)")
+        if precision not in ("fp32", "bf16", "fp8", "mxfp8"):
+            raise ValueError("precision must be 'fp32' (exact-f32 MFMA, parity mode), 'bf16' (throughput mode), 'fp8' (bf16 "
+                             "activations, e4m3 operands for the forward / data-gradient GEMMs, bf16 weight-gradient GEMMs) or 'mxfp8' "
+                             "(bf16 mode with OCP MX fp8 operands for the q/k/v, fc1 and fc2 GEMMs and the fc1 / fc2 data-gradients)")
         self.rvfm = rvfm
         self.dtype = torch.float32 if precision == "fp32" else torch.bfloat16
         self.precision = precision
@@ -326,6 +330,9 @@ class StudentEngine:
         self._opcache: Dict[str, torch.Tensor] = {}
         self._fp8_wbatch = None  # ops.QuantBatch over the weight operands (built with the operand table)
         self._fp8_conv_bf16: Dict[Any, bool] = {}  # fp8 mode: (weight key, M) -> this convolution stays on the bf16 3x3 kernel
+        # mxfp8 mode: the weight operands with MX copies (key + ".mxq" elements, key + ".mxs" scales), rebuilt by ONE launch
+        self._mx8_keys = frozenset(f"l{i}.{w}" for i in range(NUM_LAYERS) for w in MX8_WEIGHTS) if precision == "mxfp8" else frozenset()
+        self._mx8_wbatch = None
         self._opkey = None
         self._op_ptr_key = None
         self._opbatch = None
@@ -511,7 +518,20 @@ class StudentEngine:
             if self.precision == "fp8":
                 self.fp8 = Fp8Scales(device)
                 self._fp8_wbatch = None
+            self._mx8_wbatch = None
         self._opbatch.run()
+        if self._mx8_keys:
+            # MX copies of the covered weight operands, quantised from their bf16 copies: the scales come from each block's own data,
+            # so there is no state to carry between steps and the rebuild is the same launch on every step (and in a capture)
+            if self._mx8_wbatch is None:
+                mb = ops.Mx8Batch(device)
+                for k in sorted(self._mx8_keys):
+                    w = self._opcache[k]
+                    q = self._opcache[k + ".mxq"] = torch.empty(w.shape, dtype=torch.uint8, device=device)
+                    sc = self._opcache[k + ".mxs"] = torch.empty(w.shape[0], w.shape[1] // 32, dtype=torch.uint8, device=device)
+                    mb.add(w, q, sc)
+                self._mx8_wbatch = mb
+            self._mx8_wbatch.run()
         if self.fp8 is not None:
             # delayed scaling: last step's maxima become this step's scales; then the e4m3 copies of every GEMM weight operand
             # (forward W and data-gradient W^T / packed convolution weights) are re-quantised from their bf16 operands
@@ -568,6 +588,11 @@ class StudentEngine:
             return ops.linear(x8, oc[key + ".f8"], bias, scale_inv=(inv, oc[key + ".inv"]), out8=o8, **epi)
         if out8 is not None:
             out8[0] = None  # a bf16 launch: the consumer quantises its input itself
+        # mxfp8 mode: the covered weights run on MX operands (the activation through its own quantise pass); a launch beyond the
+        # kernel's 2^24 rows keeps its bf16 operands, as above
+        if key in self._mx8_keys and "out" not in epi and x.shape[0] < (1 << 24):
+            xq, xs = ops.quantize_mx8(x)
+            return ops.linear_mx8(xq, xs, oc[key + ".mxq"], oc[key + ".mxs"], bias, **epi)
         return ops.linear(x, oc[key], bias, **epi)
 
     def _build_operand_table(self, device):

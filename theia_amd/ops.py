@@ -254,6 +254,85 @@ class QuantBatch:
         N.check(N.lib().theia_quantize_fp8_batch(self._dev.data_ptr(), len(self.jobs), self._blocks, N.stream_ptr()), "theia_quantize_fp8_batch")
 
 
+def quantize_mx8(x: torch.Tensor, out: Optional[torch.Tensor] = None,
+                 scales: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [rows, K] (bf16 / f32, row stride x.stride(0), K a multiple of 32) -> (uint8 e4m3 elements [rows, K], uint8 E8M0 scales
+    [rows, K/32]): OCP MX fp8 with one power-of-two scale per 32 consecutive elements of a row (format: include/theia_hip.h)."""
+    rows, K = x.shape
+    if out is None:
+        out = torch.empty(rows, K, dtype=torch.uint8, device=x.device)
+    if scales is None:
+        scales = torch.empty(rows, K // 32, dtype=torch.uint8, device=x.device)
+    assert x.stride(1) == 1 and out.is_contiguous() and scales.is_contiguous() and out.shape == (rows, K) and scales.shape == (rows, K // 32)
+    N.check(N.lib().theia_quantize_mx8(x.data_ptr(), _dt(x), rows, K, x.stride(0), out.data_ptr(), scales.data_ptr(), N.stream_ptr()),
+            "theia_quantize_mx8")
+    return out, scales
+
+
+class Mx8Batch:
+    """A table of MX fp8 quantisations executed by ONE launch (theia_quantize_mx8_batch): the MX copies of the weight operands,
+    rebuilt after each optimizer step.  add() while building, then run() any number of times; bound to the data pointers it was
+    built with."""
+
+    def __init__(self, device):
+        self.device = device
+        self.jobs: List[N.Mx8Job] = []
+        self._dev: Optional[torch.Tensor] = None
+        self._blocks = 0
+        self._keep: List[torch.Tensor] = []
+
+    def add(self, src: torch.Tensor, dst: torch.Tensor, scales: torch.Tensor) -> None:
+        rows, K = src.shape
+        assert src.stride(1) == 1 and dst.is_contiguous() and scales.is_contiguous()
+        assert dst.shape == (rows, K) and scales.shape == (rows, K // 32) and self._dev is None
+        j = N.Mx8Job()
+        j.src, j.dst, j.dst_scale, j.rows, j.K, j.src_dtype, j.ld = src.data_ptr(), dst.data_ptr(), scales.data_ptr(), rows, K, _dt(src), src.stride(0)
+        self.jobs.append(j)
+        self._keep += [src, dst, scales]
+
+    def run(self) -> None:
+        if not self.jobs:
+            return
+        if self._dev is None:
+            import ctypes
+            arr = (N.Mx8Job * len(self.jobs))(*self.jobs)
+            self._blocks = N.lib().theia_quantize_mx8_batch_plan(ctypes.addressof(arr), len(self.jobs))
+            if self._blocks <= 0:
+                N.check(int(self._blocks), "theia_quantize_mx8_batch_plan")
+            raw = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr))), dtype=torch.uint8)
+            self._dev = raw.to(self.device)
+        N.check(N.lib().theia_quantize_mx8_batch(self._dev.data_ptr(), len(self.jobs), self._blocks, N.stream_ptr()), "theia_quantize_mx8_batch")
+
+
+def gemm_nt_mx8(a: torch.Tensor, a_scale: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, out: torch.Tensor,
+                bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, act: int = N.ACT_NONE,
+                aux_in: Optional[torch.Tensor] = None, aux_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [M, N] (bf16) = act(A @ W^T + bias) + resid with MX fp8 operands (quantize_mx8): A [M, K] / W [N, K] uint8 with
+    row strides, scales [M, K/32] / [N, K/32]; resid / aux_in / aux_out share out's row stride (theia_gemm_nt_mx8)."""
+    M, K = a.shape
+    Nn = w.shape[0]
+    assert a.dtype == w.dtype == a_scale.dtype == w_scale.dtype == torch.uint8 and out.dtype == torch.bfloat16
+    assert w.shape[1] == K and a_scale.shape == (M, K // 32) and w_scale.shape == (Nn, K // 32) and out.shape == (M, Nn)
+    assert a.stride(1) == w.stride(1) == out.stride(1) == 1 and a_scale.is_contiguous() and w_scale.is_contiguous()
+    for t in (resid, aux_in, aux_out):
+        assert t is None or (t.dtype == torch.bfloat16 and t.shape == out.shape and t.stride() == out.stride())
+    g = N.Mx8GemmArgs()
+    g.a, g.a_scale, g.w, g.w_scale, g.out = a.data_ptr(), a_scale.data_ptr(), w.data_ptr(), w_scale.data_ptr(), out.data_ptr()
+    g.bias, g.resid, g.aux_in, g.aux_out = N.ptr(bias), N.ptr(resid), N.ptr(aux_in), N.ptr(aux_out)
+    g.M, g.N, g.K, g.lda, g.ldw, g.ldo, g.act = M, Nn, K, a.stride(0), w.stride(0), out.stride(0), act
+    N.check(N.lib().theia_gemm_nt_mx8(g, N.stream_ptr()), "theia_gemm_nt_mx8")
+    return out
+
+
+def linear_mx8(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias: Optional[torch.Tensor] = None,
+               resid: Optional[torch.Tensor] = None, act: int = N.ACT_NONE, aux_in: Optional[torch.Tensor] = None,
+               aux_out: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ops.linear on MX fp8 operands: (xq, xs) = quantize_mx8(x), (wq, ws) = quantize_mx8(w) -> bf16 [M, N]"""
+    if out is None:
+        out = torch.empty(xq.shape[0], wq.shape[0], dtype=torch.bfloat16, device=xq.device)
+    return gemm_nt_mx8(xq, xs, wq, ws, out, bias, resid, act, aux_in, aux_out)
+
+
 def fp8_update_scales(amax: torch.Tensor, scale: torch.Tensor, inv_scale: torch.Tensor, margin: float = 1.0) -> None:
     """delayed scaling: scale = 448 / (amax * margin) for every slot that saw data, inv_scale = 1 / scale, amax = 0"""
     N.check(N.lib().theia_fp8_update_scales(amax.data_ptr(), scale.data_ptr(), inv_scale.data_ptr(), amax.numel(), margin, N.stream_ptr()),
